@@ -2,12 +2,22 @@
 """bench.py — gates/sec through (topo-sort + wire numbering + gate emission + boolify) on the synthetic
 10 M-gate DAG of BASELINE.json (configs[4]), device-resident in / device-resident out.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--width 32] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N ...
 
 A "step" = one pass of the hot path over ONE gate graph already resident in HBM: c2a_build_circuit (sort,
 numbering, emission) + c2a_boolify(width).
+
+A plain run does only what the headline needs: generate the graph, the cold single shot (`cold`), load the graph, W
+warm-up steps, K timed steps, the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the stage
+split and the whole-step roofline under the committed PMC profile).  The cold shot stays because the headline has always
+been timed on the process's second context: timed on the first, `prep` takes ~0.17 ms (1.5 % of the step) longer on an
+MI355X, whatever the warm-up.  `--full` adds everything else listed below — the oracle check, the live PMC passes, the CPU
+baseline, width 64, the reference-shaped graph, BASELINE's small configs, artefacts, prune and, for N > 1 in `--mode both`,
+the replicas region; the `--no-*` options leave single parts out.  `--check` asks for the oracle check in a plain run
+too.  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs) after the timed steps; the input is
+generated from a fixed seed, so two builds run with the same arguments can be compared file by file.
 
 N > 1 (default `--mode shard`): still ONE 10 M-gate graph — BASELINE's metric.  The sort is a chain of ~5 000
 dependent steps and does not shard, so every rank sorts the same graph and bit-blasts only its own
@@ -15,7 +25,7 @@ sorted-position range (no data-path collective: each rank holds the whole sorted
 value = n / max-over-ranks time; the line says what bounds it (`config.strong_scaling_bound`).  `--mode replicas` is
 the explicitly named throughput mode: N independent graphs, one per GPU, `"scaling": "weak"`.
 
-One JSON line on stdout (rank 0):
+One JSON line on stdout (rank 0); the parts after the first only with `--full`:
   * `roofline` describes the WHOLE timed step: achieved = (30 n + sum_g (13 + 13 T(op_g, w))) bytes
     / ms_per_step, against the 8 TB/s HBM spec; `roofline.kernels` has one entry per dominant kernel (the dataflow
     peel, the boolify map) with its own algorithmic bytes, its launch time from HIP events on the library's stream,
@@ -192,6 +202,44 @@ def check_against_oracle(be, backend_mod, circ, width, shard=None, slice_gates=2
     return msg
 
 
+DUMP_BLOCKS, DUMP_BLOCK = 128, 4096      # per circuit at most 2^19 gates: 4 arrays + positions, float64 = 20 MB; 40 MB in all
+
+
+def sample_positions(total, seed):
+    """All of [0, total) when it fits DUMP_BLOCKS x DUMP_BLOCK, otherwise one block of DUMP_BLOCK consecutive positions at a
+    seeded offset inside each of DUMP_BLOCKS equal strata: a fixed sample spread over the whole output.  Returns (start, len) pairs."""
+    if total <= DUMP_BLOCKS * DUMP_BLOCK:
+        return [(0, total)]
+    stratum = total // DUMP_BLOCKS
+    offs = np.random.default_rng(seed).integers(0, stratum - DUMP_BLOCK + 1, DUMP_BLOCKS)
+    return [(k * stratum + int(o), DUMP_BLOCK) for k, o in enumerate(offs)]
+
+
+def dump_outputs(be, info, out_dir):
+    """What the caller of the timed path receives from its last step, as float64 .npy files (every u32 / u8 value is exact):
+    the boolean circuit of c2a_boolify (c2a_bool_read) and the arithmetic circuit of c2a_build_circuit (c2a_emit_gates),
+    each over the positions of sample_positions (`*_pos.npy`), plus `counts.npy` = [gates, wires, boolean gates, boolean
+    wires].  The boolean gates are read first: c2a_emit_gates re-runs the emission kernel on the resident sort and numbering
+    (same inputs, same gates) and leaves the context without a boolean circuit."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+    def save_circuit(prefix, blocks, arrays):
+        save(prefix + "_pos", np.concatenate([np.arange(s, s + ln) for s, ln in blocks]))
+        for name, a in zip(("in0", "in1", "out", "op"), arrays):
+            save(f"{prefix}_{name}", a)
+
+    blocks = sample_positions(info.n_gates, seed=1)
+    reads = [be.bool_read(s, ln) for s, ln in blocks]
+    save_circuit("bool", blocks, [np.concatenate([r[k] for r in reads]) for k in range(4)])
+    blocks = sample_positions(be.n, seed=2)
+    emitted = be.emit_gates()
+    save_circuit("arith", blocks, [np.concatenate([a[s:s + ln] for s, ln in blocks]) for a in emitted])
+    save("counts", [be.n, be.wire_count, info.n_gates, info.wire_count])
+
+
 def cpu_baseline(fg, width, chunk_gates, circ, handle, t_flat):
     """CPU oracle on the host cores of this box, 1 thread, the whole benchmark input: the structure-faithful
     build_circuit (hash maps, per-visit Vec: THE baseline) and the flat-array one (second row), and the bit-blast of every sorted
@@ -335,8 +383,17 @@ def main():
                     help="N>1: 'shard' = ONE graph, sort replicated on every rank, boolify sharded by sorted-position range (strong "
                          "scaling, BASELINE's metric: the line's `value`); 'replicas' = N independent graphs, one per GPU (throughput, "
                          "weak); 'both' (default) = the shard region, then the replicas region in the same process, reported as "
-                         "`aggregate_replicas` beside `value`")
+                         "`aggregate_replicas` beside `value` (with --full; a plain run times the shard region only)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures or checks (module docstring); the --no-* "
+                         "options leave single parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (float64, a fixed sample of the "
+                         "boolean and the arithmetic circuit, 40 MB at most; rank 0)")
     args = ap.parse_args()
+    if not args.full:            # a plain run: setup (the cold shot included, module docstring), warm-up, the timed steps, the line
+        args.no_cpu_baseline = args.no_live_pmc = args.no_width64 = args.no_artefacts = args.no_prune = True
+        args.no_reference_shaped = args.no_configs = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -371,7 +428,10 @@ def main():
 
     shard = args.mode in ("shard", "both") and world > 1
     replicas = args.mode == "replicas" and world > 1
-    both = args.mode == "both" and world > 1
+    both = args.mode == "both" and world > 1 and args.full
+    if args.dump_outputs and shard:
+        # (a rank's boolean gates of the shard step stay in a chunk buffer that no call reads back without computing them again)
+        sys.exit("bench.py --dump-outputs: one process, or --mode replicas")
     t0 = time.time()
     fg = synth.layered_dag(args.layers, args.layer_width, seed=synth.SEED + (rank if replicas else 0))
     gen_s = time.time() - t0
@@ -438,6 +498,8 @@ def main():
     if want_oracle and not replicas or (replicas and args.check):
         circ, handle, t_oracle_build = oracle_circuit(fg)
         checked = check_against_oracle(be, backend_mod, circ, args.width, shard=last.get("range") if shard else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(be, info, args.dump_outputs)
     # ---- N > 1, mode both: the SAME launch also answers the throughput question — every rank now takes an independent graph of
     # its own (seed + rank), the whole pipeline per GPU, no exchange: N graphs / max-over-ranks time (weak scaling).  north_star's
     # ">= 6x aggregate at 8 GPUs" can only be met here: the one-graph number above is bounded by the replicated sort

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 for v in "$@"; do cp build_ab/$v.so circom-2-arithc_amd/libc2a_hip.so; echo "== $v"
   timeout 600 python tools/bool_by_op.py 32 2>&1 | grep -v "^\[c2a" | cut -c1-150
   timeout 300 python tools/bool_ramp.py 2>&1 | grep -v "^\[c2a"
-  timeout 600 python bench.py --steps 3 --warmup 1 --no-cold --no-width64 --no-artefacts --no-prune --no-live-pmc --no-cpu-baseline --no-reference-shaped 2>/dev/null | python3 -c "
+  timeout 600 python bench.py --steps 3 --warmup 1 --no-cold --no-width64 --no-artefacts --no-prune --no-live-pmc --no-cpu-baseline --no-reference-shaped --full 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
